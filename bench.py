@@ -22,6 +22,16 @@ Synthetic data: 65,536 distinct keys and 200-byte random messages per rank
 tools/synth.py (our own code; the oracle is used only by cpu_baseline), one
 arena record per signature.
 
+A plain run (`--gpus 1 --steps K --warmup W`) does what the headline figure
+needs and no more: set up, prime + warm up, time the K steps, drain and check
+the codes, print the line.  `--full` adds the measurements that take runs of
+their own: each launch alone between two events after the timed region
+(roofline.kernel_ms / kernel_frac) and cpu_baseline; without it those keys
+are null.  `--dump-outputs DIR` writes the last timed step's results to
+DIR/verify.npy (float32 [n, 2]: verified 1.0 / 0.0, and the code; the output
+buffers start at a poison value, so an unwritten element is not a zero);
+inputs are seeded, so two builds compare output for output.
+
 Extra keys beside the contract fields:
   roofline     -- INT32 VALU multiply-add roofline of the verify kernel
                   (SURVEY.md §8(d)): achieved = W MAC/verify x verifies per launch
@@ -37,7 +47,7 @@ Extra keys beside the contract fields:
   cpu_baseline -- the reference fd_ed25519_verify (AVX-512 build when the host
                   has avx512ifma, else the portable build) compiled from the
                   reference sources (oracle/_ref), on a bounded sample of the
-                  same descriptors, on this host's cores (rank 0, N=1 only).
+                  same descriptors, on this host's cores (rank 0, N=1, --full only).
 """
 import argparse
 import ctypes
@@ -100,6 +110,21 @@ def build_adversarial(n):
     hist = {int(k): int(v) for k, v in zip(*np.unique(exp, return_counts=True))}
     return arena, desc, sz, exp, "config-4 adversarial mix: %d golden records (reference vectors + generated " \
         "classes) tiled to %d, expected codes %s" % (len(base), n, hist)
+
+
+POISON = 0x55    # no FD_ED25519_* code: what an output element holds until a launch writes it
+
+
+def dump_output(dirname, name, codes):
+    """--dump-outputs: the last timed step's per-signature results as
+    DIR/<name>.npy, float32 [n, 2]: column 0 is 1.0 where the signature
+    verified (code FD_ED25519_SUCCESS = 0) and 0.0 where not, column 1 the
+    code itself.  The benchmark's batch is all valid, so its codes alone
+    would be a file of zeros; the output buffers start at POISON, so an
+    element no launch wrote reads as not verified."""
+    codes = np.asarray(codes).astype(np.int8)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + ".npy"), np.stack([codes == 0, codes], axis=1).astype(np.float32))
 
 
 def valu_peak():
@@ -351,13 +376,20 @@ def notorch_main(args):
     h2d(d_arena, arena)
     h2d(d_desc, np.ascontiguousarray(desc))
     d_outs = [dmalloc(n), dmalloc(n)]
+    d_after = [dmalloc(n), dmalloc(n)]     # the launches after the timed region write these (--dump-outputs)
+    for d in d_outs + d_after:
+        assert hip.hipMemset(vp(d), POISON, sz_t(n)) == 0
+    assert hip.hipDeviceSynchronize() == 0
     stream = vp()
     assert hip.hipStreamCreateWithFlags(ctypes.byref(stream), 1) == 0      # non-blocking, like torch's side stream
     g = fa.Ed25519Gpu(device_mask=1, max_batch=n)
     nstep = [0]
 
-    def step():
-        g.pipe_dev(d_arena, sz, d_desc, n, d_outs[nstep[0] & 1], stream=stream.value)
+    written = set()      # the output buffers some step wrote
+
+    def step(outs=d_outs):
+        written.add(outs[nstep[0] & 1])
+        g.pipe_dev(d_arena, sz, d_desc, n, outs[nstep[0] & 1], stream=stream.value)
         nstep[0] += 1
 
     def sync():
@@ -391,19 +423,22 @@ def notorch_main(args):
     sync()
     dt = time.perf_counter() - t0
     region_ms = elapsed(ev0, ev1) / args.steps
+    d_last = d_outs[(nstep[0] - 1) & 1]                  # where the last timed step's codes land
     evs = [(event(), event()) for _ in range(min(args.steps, 50))]
     for a, b in evs:
         hip.hipEventRecord(a, stream)
-        step()
+        step(d_after)
         hip.hipEventRecord(b, stream)
     sync()
     launch_ms = float(np.mean([elapsed(a, b) for a, b in evs]))
     g.pipe_flush_dev(stream=stream.value)
     sync()
-    for d in d_outs:
+    for d in [d for d in d_outs + d_after if d in written]:
         o = np.zeros(n, np.int8)
         assert hip.hipMemcpy(vp(o.ctypes.data), vp(d), sz_t(n), 2) == 0
         assert np.array_equal(o, expect), "verify codes differ from the expected ones"
+        if args.dump_outputs and d == d_last:
+            dump_output(args.dump_outputs, "verify", o)
     value = n * args.steps / dt
     peak = valu_peak()
     line = {"metric": "Ed25519 verifies/sec (no torch in the process)", "value": value, "unit": "verifies/s",
@@ -417,7 +452,7 @@ def notorch_main(args):
             "warmup_detail": {"prime_steps": prime, "warmup_steps": args.warmup},
             "build": fa.build_id(), "runtime": fa.runtime_info(), "torch_loaded": "torch" in sys.modules}
     g.close()
-    for d in [d_arena, d_desc] + d_outs:
+    for d in [d_arena, d_desc] + d_outs + d_after:
         hip.hipFree(vp(d))
     hip.hipStreamDestroy(stream)
     print(json.dumps(line), flush=True)
@@ -462,13 +497,15 @@ def shred_main(args):
             assert np.all(out == 0), "shred codes differ from the reference's (all valid)"
             t0 = time.perf_counter()
             for _ in range(steps):
-                g.shred_verify(arena, len(arena), aux_off, 32 * n, spans, keys)
-            return (time.perf_counter() - t0) / steps
+                out = g.shred_verify(arena, len(arena), aux_off, 32 * n, spans, keys)
+            return (time.perf_counter() - t0) / steps, out
         finally:
             os.environ.pop("FD_ED25519_GPU_SHRED_HOST_HASH", None)
 
-    t_gpu = timed(False, args.steps)
-    t_host = timed(True, max(args.steps // 4, 3))
+    t_gpu, codes = timed(False, args.steps)
+    if args.dump_outputs:
+        dump_output(args.dump_outputs, "shred_verify", codes)
+    t_host, _ = timed(True, max(args.steps // 4, 3))
     host = arena.copy()
     t0 = time.perf_counter()
     walks = 3
@@ -560,10 +597,23 @@ def main():
                          "(sync calls and the async submit/poll stream, pageable and page-locked) beside the H2D "
                          "bandwidth, N=1, a line of its own.  no-torch: the config-2 step with no torch in the "
                          "process (device memory, stream and events from the library's own HIP runtime), N=1")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure, also measure what takes runs of its own: each launch alone "
+                         "between two events after the timed region (roofline.kernel_ms, kernel_frac) and the "
+                         "reference's CPU baseline (cpu_baseline, unless --no-cpu).  Off by default: a plain run "
+                         "sets up, warms up, times the steps and prints the line, with those keys null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed -- per signature, "
+                         "whether it verified (1.0 / 0.0) and its code, as a caller of the step receives them -- to "
+                         "DIR/verify.npy (float32 [n, 2]; rank r > 0 of a multi-GPU run: DIR/verify_rank<r>.npy; "
+                         "--path shred: shred_verify.npy).  The inputs are seeded, so two builds run with the same "
+                         "arguments can be compared output for output")
     ap.add_argument("--stub", action="store_true",
                     help="CPU test mode (tests/test_bench_launch.py): gloo, a no-op step on a fixed count; "
                          "exercises the launcher, rank setup and SUM/MAX aggregation without a GPU")
     args = ap.parse_args()
+    if args.dump_outputs and (args.stub or args.path == "host-fed"):
+        ap.error("--dump-outputs: --stub computes nothing and --path host-fed has no single timed step to dump")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args))
@@ -628,25 +678,32 @@ def main():
         data_desc += "; all %d signers in the hot-key cache" % len(keys)
     d_arena = torch.from_numpy(arena).to(dev)
     d_desc = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
-    d_out = torch.zeros(n, dtype=torch.int8, device=dev)
+    d_out = torch.full((n,), POISON, dtype=torch.int8, device=dev)
     stream = torch.cuda.Stream(device=dev)
     torch.cuda.set_stream(stream)
     pair_max = 256 * torch.cuda.get_device_properties(dev).multi_processor_count   # the host's pair_max
     pipe = (args.pipeline == 1 or (args.pipeline == -1 and n <= pair_max)) and not args.hot_keys
-    d_outs = [d_out, torch.zeros(n, dtype=torch.int8, device=dev)]
+    d_outs = [d_out, torch.full((n,), POISON, dtype=torch.int8, device=dev)]
+    # --full: the launches after the timed region write buffers of their own, so
+    # the last timed step's codes stay as that step left them (--dump-outputs)
+    d_after = [torch.full((n,), POISON, dtype=torch.int8, device=dev) for _ in range(2)] if args.full else []
+    torch.cuda.synchronize()     # the fills ran on the default stream, the steps run on `stream`
     nstep = [0]
+    written = set()      # the output buffers some step wrote: the ones whose codes the drain checks
 
-    def step():
-        # pipelined: step i's codes land in d_outs[i % 2] once the launches two
+    def step(outs=d_outs):
+        # pipelined: step i's codes land in outs[i % 2] once the launches two
         # chunks later complete; a batch above one wave per SIMD (config 3) is
         # the library's k pre-pass + one launch per pair_max chunk, three chunks
         # in flight across launches and across steps
         if pipe:
-            out = d_outs[nstep[0] & 1]
+            out = outs[nstep[0] & 1]
+            written.add(out.data_ptr())
             g.pipe_dev(d_arena.data_ptr(), sz, d_desc.data_ptr(), n, out.data_ptr(), stream=stream.cuda_stream)
             nstep[0] += 1
             return
-        g.verify_batch_dev(d_arena.data_ptr(), sz, d_desc.data_ptr(), n, d_out.data_ptr(),
+        written.add(outs[0].data_ptr())
+        g.verify_batch_dev(d_arena.data_ptr(), sz, d_desc.data_ptr(), n, outs[0].data_ptr(),
                            stream=stream.cuda_stream)
 
     def settle():
@@ -657,7 +714,7 @@ def main():
             g.pipe_flush_dev(stream=stream.cuda_stream)
         torch.cuda.synchronize()
         t = time.perf_counter() - t
-        for o in (d_outs if pipe else [d_out]):
+        for o in [o for o in d_outs + d_after if o.data_ptr() in written]:
             assert np.array_equal(o.cpu().numpy(), expect), "verify codes differ from the expected ones"
         return t
 
@@ -687,16 +744,23 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     region_ms = ev0.elapsed_time(ev1) / args.steps    # average launch duration over the region, gaps included
-    # after the region (untimed): each launch alone between two events, for
-    # the kernel's own duration (kernel_ms, kernel_frac)
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(min(args.steps, 50))]
-    for a, b in ev:
-        a.record(stream)
-        step()
-        b.record(stream)
-    torch.cuda.synchronize()
-    launch_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
+    d_last = d_outs[(nstep[0] - 1) & 1] if pipe else d_out   # where the last timed step's codes land
+    # --full, after the region (untimed): each launch alone between two events,
+    # for the kernel's own duration (kernel_ms, kernel_frac)
+    launch_ms = None
+    if args.full:
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+              for _ in range(min(args.steps, 50))]
+        for a, b in ev:
+            a.record(stream)
+            step(d_after)
+            b.record(stream)
+        torch.cuda.synchronize()
+        launch_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     drain = settle()
+    if args.dump_outputs:
+        # the last timed step's codes (pipelined: final once the drain has run)
+        dump_output(args.dump_outputs, "verify" if rank == 0 else "verify_rank%d" % rank, d_last.cpu().numpy())
 
     from firedancer_amd.dist import aggregate_throughput
     total, dt_max = aggregate_throughput(n * args.steps, dt, device=dev)
@@ -716,7 +780,7 @@ def main():
         # per GPU), as `value` is; the event-bracketed kernel time gives
         # kernel_frac beside it
         achieved = W_MAC * value / world
-        kernel_achieved = W_MAC * n / (launch_ms * 1e-3)
+        kernel_frac = W_MAC * n / (launch_ms * 1e-3) / peak if args.full else None
         build = fa.build_id()
         traffic, traffic_src = pmc_traffic(n, kname, build.get("code")) if args.config == 2 else (None, "config 2 only")
         line = {
@@ -726,6 +790,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": dt_max / args.steps * 1e3,
             "higher_is_better": True,
             "scaling": "strong" if args.config == 3 else "weak",
@@ -741,9 +806,10 @@ def main():
                          "region_ms_per_launch": region_ms,
                          "region_ms_note": "HIP events on the launch stream around the timed region / steps: the "
                                            "average launch duration, inter-launch gaps included",
-                         "kernel_ms": launch_ms, "kernel_frac": kernel_achieved / peak,
+                         "kernel_ms": launch_ms, "kernel_frac": kernel_frac,
                          "kernel_frac_note": "the same W priced on the mean event-bracketed launch (no inter-launch "
-                                             "gap), measured over up to 50 launches right after the timed region"},
+                                             "gap), measured over up to 50 launches right after the timed region "
+                                             "(--full; null otherwise)"},
             "cpu_baseline": None,
             "warmup_detail": {"prime_steps": prime, "prime_ms": args.prime_ms, "warmup_steps": args.warmup,
                               "untimed_steps_total": prime + args.warmup,
@@ -772,7 +838,7 @@ def main():
                                     "frac": gbs / 8000.0, "traffic": t}
         if args.config != 2:   # the roofline numerator W is defined for valid 200-B verifies only
             line["roofline"]["frac_note"] = "W-based numerator is for valid 200-B verifies (config 2)"
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             line["cpu_baseline"] = cpu_baseline(arena, desc, expect, args.cpu_budget)
         print(json.dumps(line), flush=True)
     g.close()

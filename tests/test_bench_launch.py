@@ -3,11 +3,14 @@ runs N ranks itself (torch.distributed.run child, one process per GPU) and
 reports the whole-job value (SUM of units over ranks / MAX of time); a box
 with fewer devices than N is refused, never measured as one GPU.  --stub
 replaces the GPU step with a CPU sleep (gloo), so the launcher, rank setup and
-aggregation run here exactly as on the GPU node."""
+aggregation run here exactly as on the GPU node.  One GPU test runs a small
+plain line: no --full measurements in it, and --dump-outputs writes the codes."""
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -58,6 +61,36 @@ def test_too_few_gpus_refused():
     assert r.returncode == 2
     assert "refusing" in r.stderr
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_dump_outputs_refused_where_nothing_is_computed(tmp_path):
+    # --stub computes no codes: asking for them is an error, not an empty directory
+    r = _run(["--gpus", "1", "--stub", "--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path / "d")])
+    assert r.returncode == 2
+    assert "--dump-outputs" in r.stderr
+    assert not (tmp_path / "d").exists()
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_last_step_codes(tmp_path):
+    """A plain run (no --full) measures the headline only -- kernel_ms,
+    kernel_frac and cpu_baseline are null -- and --dump-outputs writes the
+    last timed step's results: float32 [n, 2], per signature verified (1.0)
+    and its code (0)."""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--prime-ms", "0", "--batch", "4096",
+              "--dump-outputs", str(out)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _line(r.stdout)
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["full"] is False
+    assert abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert d["roofline"]["kernel_ms"] is None and d["roofline"]["kernel_frac"] is None
+    assert d["cpu_baseline"] is None
+    res = np.load(out / "verify.npy")
+    assert res.dtype == np.float32 and res.shape == (4096, 2)
+    assert np.all(res[:, 0] == 1.0)          # every signature verified: written by a launch, not the buffers' poison
+    assert not res[:, 1].any()               # and its code is FD_ED25519_SUCCESS
 
 
 def test_world_size_mismatch_refused():

@@ -63,6 +63,7 @@ case "$cmd" in
     done
     python3 tools/phase_bytes.py --summarize $o/*/pmc_counter_collection.csv | tee gpurun_out/phasebytes_$T.json ;;
   bench)
+    set -- --full "$@"      # the line with kernel_ms and the CPU baseline
     timeout -k 10 300 python3 bench.py "$@" > gpurun_out/bench_$T.json 2> gpurun_out/bench_$T.err \
       || { tail -20 gpurun_out/bench_$T.err; exit 1; }
     cat gpurun_out/bench_$T.json ;;
@@ -71,6 +72,7 @@ case "$cmd" in
     # --stats average is the steady state (the prime / warm-up launches at a ramping clock are few)
     cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
     o=gpurun_out/prof_$T; mkdir -p $o
+    set -- --full "$@"      # tools/summarize_profile.py reads roofline.kernel_ms
     timeout -k 10 300 python3 bench.py "$@" > $o/bench.json 2> $o/bench.err
     timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 "$@" > $o/bench_driver_form.json 2> $o/bench_driver_form.err
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $o/kt -o kt -- \
