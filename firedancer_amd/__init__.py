@@ -18,6 +18,7 @@ from .ed25519 import (  # noqa: F401
     QUEUE_DEPTH,
     STAGE_DEPTH,
     GOSSIP_NO_VALUES,
+    SIGN_DESC_DTYPE, pack_sign_batch,
     shred_walk, sha256, SHRED_PARSE, SHRED_ZERO_SIG, SHRED_COUNTS, SHRED_INDEX, SHRED_DEPTH, SHRED_PROOF,
 )
 from .verify_stage import (  # noqa: F401

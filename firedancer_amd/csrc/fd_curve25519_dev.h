@@ -191,6 +191,21 @@ FD_GE_FN void fe_invert( fe & out, fe const & z ) {
   FE_FENCE();
 }
 
+/* Point compression (replaces fd_ed25519_point_tobytes,
+   src/ballet/ed25519/fd_curve25519.c): o = 8 LE words of the canonical
+   y = Y / Z with bit 255 = the parity of the canonical x = X / Z.  p.X, p.Y,
+   p.Z in R (T is not read). */
+FD_GE_FN void ge_tobytes( uint32_t o[ 8 ], ge_p3 const & p ) {
+  fe zi, x, y;
+  fe_invert( zi, p.Z );
+  fe_mul( x, p.X, zi );
+  FE_FENCE();
+  fe_mul( y, p.Y, zi );
+  FE_FENCE();
+  fe_tobytes32( o, y );
+  o[7] |= (uint32_t)fe_sgn( x ) << 31;
+}
+
 /* Point decompression.  w: 8 LE words of the 32-byte encoding.  Returns 1
    on success.  Semantics: y = w with bit 255 cleared
    (not reduced), u = y^2-1, v = dy^2+1, x = uv^3 (uv^7)^((p-5)/8); fail if

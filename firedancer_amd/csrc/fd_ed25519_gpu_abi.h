@@ -296,6 +296,28 @@ struct len_args {
   uint32_t *                idx;      /* n: descriptor indices, bucket order per segment */
 };
 
+/* Batch signing and key derivation (fd_ed25519_sign_kern.hip): one
+   signature or key per lane, out and prv 4-byte aligned. */
+struct sign_args {
+  uint8_t const *                arena;
+  uint64_t                       arena_sz;
+  fd_ed25519_sign_desc_t const * desc;
+  uint64_t                       n;
+  uint32_t *                     out;       /* 16 words (R || S) per descriptor */
+  uint32_t const *               ctab;      /* fixed-base comb table */
+};
+struct sign_pubkey_args {
+  uint32_t const *               prv;       /* 8 words per key */
+  uint64_t                       n;
+  uint32_t *                     out;       /* 8 words per key */
+  uint32_t const *               ctab;
+};
+#define FD_KERN_SIGN     "fd_ed25519_sign_kernel"
+#define FD_KERN_PUBKEY   "fd_ed25519_pubkey_kernel"
+#ifndef FD_SIGN_WAVES_PER_EU
+#define FD_SIGN_WAVES_PER_EU 2          /* <= 256 VGPRs per lane: both kernels build without scratch */
+#endif
+
 /* Seeded key hash shared by the host (slot assignment) and the device
    (lookup): splitmix64 of the key's first 8 bytes xor seed. */
 static inline

@@ -101,6 +101,47 @@ FD_SC_FN void sc_reduce512( uint32_t r[ 8 ], uint32_t const x[ 16 ] ) {
   for( int i=0; i<8; i++ ) r[i] = t9[i];
 }
 
+/* r = x mod l for a 256-bit x (8 LE words): the signer's clamped secret
+   scalar a in [2^254, 2^255) is always >= l, comb_bias wants w < l, and
+   [a]B = [a mod l]B.  q = x >> 252 <= 15 and x - q l = (x mod 2^252) - q c
+   with c = l - 2^252 < 2^125, so it lies in (-2^129, 2^252): one conditional
+   addition of l brings it into [0, l). */
+FD_SC_FN void sc_reduce256( uint32_t r[ 8 ], uint32_t const x[ 8 ] ) {
+  uint32_t const l[ 8 ] = { FD_L0, FD_L1, FD_L2, FD_L3, 0u, 0u, 0u, FD_L7 };
+  uint32_t q = x[7] >> 28;
+  uint32_t t[ 8 ];
+  uint64_t c = 0, br = 0;
+#pragma unroll
+  for( int i=0; i<8; i++ ) {
+    c += (uint64_t)q * l[i];                          /* q l < 2^256 */
+    uint64_t d = (uint64_t)x[i] - (uint32_t)c - br;
+    t[i] = (uint32_t)d; br = (d >> 63) & 1u; c >>= 32;
+  }
+  uint64_t a = 0;
+#pragma unroll
+  for( int i=0; i<8; i++ ) { a += (uint64_t)t[i] + (br ? l[i] : 0u); r[i] = (uint32_t)a; a >>= 32; }
+}
+
+/* s = (k a + r) mod l for k, r < l and a < 2^255 (replaces
+   fd_curve25519_scalar_muladd, fd_curve25519_scalar.c): the 8x8-word product
+   plus r (< 2^508 + 2^253) through sc_reduce512. */
+FD_SC_FN void sc_muladd( uint32_t s[ 8 ], uint32_t const k[ 8 ], uint32_t const a[ 8 ], uint32_t const r[ 8 ] ) {
+  uint32_t x[ 16 ];
+#pragma unroll
+  for( int i=0; i<8; i++ ) { x[i] = r[i]; x[8+i] = 0u; }
+#pragma unroll
+  for( int i=0; i<8; i++ ) {
+    uint64_t c = 0;
+#pragma unroll
+    for( int j=0; j<8; j++ ) {
+      uint64_t t = (uint64_t)k[i] * a[j] + x[i+j] + c;
+      x[i+j] = (uint32_t)t; c = t >> 32;
+    }
+    x[i+8] = (uint32_t)c;
+  }
+  sc_reduce512( s, x );
+}
+
 /* Signed fixed-window recoding.  s (< 2^253) = sum_i d_i 2^(w i) with
    d_i in [-2^(w-1), 2^(w-1)-1] for all but possibly the top digit.  The
    digits are emitted as (d + 2^(w-1)) biased bytes so they fit a u8. */

@@ -35,6 +35,11 @@ DESC_DTYPE = np.dtype([("sig_off", "<u4"), ("pub_off", "<u4"), ("msg_off", "<u4"
                        ("msg_sz", "<u2"), ("txn_idx", "<u2")])
 assert DESC_DTYPE.itemsize == 16
 
+# fd_ed25519_sign_desc_t (16 bytes, include/fd_ed25519_gpu.h)
+SIGN_DESC_DTYPE = np.dtype([("prv_off", "<u4"), ("pub_off", "<u4"), ("msg_off", "<u4"),
+                            ("msg_sz", "<u2"), ("rsvd", "<u2")])
+assert SIGN_DESC_DTYPE.itemsize == 16
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
@@ -102,6 +107,10 @@ def load_lib():
     lib.fd_sha512_batch_gpu_dev.argtypes = [vp, i32, vp, u64, vp, u64, vp, vp]
     lib.fd_sha256_batch_gpu.argtypes = [vp, vp, u64, vp, u64, vp]
     lib.fd_sha256_batch_gpu_dev.argtypes = [vp, i32, vp, u64, vp, u64, vp, vp]
+    lib.fd_ed25519_gpu_sign_batch.argtypes = [vp, vp, u64, vp, u64, vp]
+    lib.fd_ed25519_gpu_sign_batch_dev.argtypes = [vp, i32, vp, u64, vp, u64, vp, vp]
+    lib.fd_ed25519_gpu_public_from_private_batch.argtypes = [vp, vp, u64, vp]
+    lib.fd_ed25519_gpu_public_from_private_batch_dev.argtypes = [vp, i32, vp, u64, vp, vp]
     lib.fd_ed25519_gpu_tcache_new.restype = vp
     lib.fd_ed25519_gpu_tcache_new.argtypes = [u64, u64]
     lib.fd_ed25519_gpu_tcache_delete.argtypes = [vp]
@@ -194,6 +203,26 @@ def pack_batch(records):
             arena[off + 96:off + 96 + len(msg)] = np.frombuffer(msg, np.uint8)
         desc[i] = (off, off + 64, off + 96, len(msg), txn)
         off += 96 + len(msg)
+    return arena, desc, total
+
+
+def pack_sign_batch(records):
+    """records: iterable of (prv, pub, msg) bytes -> (arena uint8 array, SIGN_DESC_DTYPE array, arena size).
+
+    Layout: prv | pub | msg per record, packed back to back with no alignment;
+    the last message ends on the arena's last byte."""
+    recs = list(records)
+    desc = np.zeros(len(recs), dtype=SIGN_DESC_DTYPE)
+    total = sum(64 + len(r[2]) for r in recs)
+    arena = np.zeros(total + 16, dtype=np.uint8)
+    off = 0
+    for i, (prv, pub, msg) in enumerate(recs):
+        arena[off:off + 32] = np.frombuffer(prv, np.uint8)
+        arena[off + 32:off + 64] = np.frombuffer(pub, np.uint8)
+        if msg:
+            arena[off + 64:off + 64 + len(msg)] = np.frombuffer(msg, np.uint8)
+        desc[i] = (off, off + 32, off + 64, len(msg), 0)
+        off += 64 + len(msg)
     return arena, desc, total
 
 
@@ -539,6 +568,40 @@ class Ed25519Gpu:
         if r:
             raise GpuError("%s: %s (%d)" % (name, strerror(r), r))
         return [out[dlen * i:dlen * i + dlen].tobytes() for i in range(len(msgs))]
+
+    def sign_batch(self, arena, arena_sz, desc):
+        """fd_ed25519_gpu_sign_batch: desc SIGN_DESC_DTYPE (pack_sign_batch) -> uint8 array [n, 64] of R || S.
+        Not constant time (include/fd_ed25519_gpu.h)."""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        desc = np.ascontiguousarray(desc, dtype=SIGN_DESC_DTYPE)
+        out = np.zeros((len(desc), 64), dtype=np.uint8)
+        r = self.lib.fd_ed25519_gpu_sign_batch(self.ctx, _ptr(arena), arena_sz, _ptr(desc), len(desc), _ptr(out))
+        if r:
+            raise GpuError("fd_ed25519_gpu_sign_batch: %s (%d)" % (strerror(r), r))
+        return out
+
+    def sign_batch_dev(self, d_arena, arena_sz, d_desc, desc_cnt, d_out_sig, stream=0, dev_idx=0):
+        """Device pointers (ints), enqueue only; 64 bytes per descriptor to d_out_sig."""
+        r = self.lib.fd_ed25519_gpu_sign_batch_dev(self.ctx, dev_idx, d_arena, arena_sz, d_desc, desc_cnt,
+                                                   d_out_sig, stream)
+        if r:
+            raise GpuError("fd_ed25519_gpu_sign_batch_dev: %s (%d)" % (strerror(r), r))
+
+    def public_from_private_batch(self, prv):
+        """fd_ed25519_gpu_public_from_private_batch: prv = uint8 array [n, 32] (or n*32 bytes) -> uint8 array [n, 32]."""
+        prv = np.ascontiguousarray(np.frombuffer(prv, np.uint8) if isinstance(prv, (bytes, bytearray)) else prv,
+                                   dtype=np.uint8).reshape(-1, 32)
+        out = np.zeros((len(prv), 32), dtype=np.uint8)
+        r = self.lib.fd_ed25519_gpu_public_from_private_batch(self.ctx, _ptr(prv), len(prv), _ptr(out))
+        if r:
+            raise GpuError("fd_ed25519_gpu_public_from_private_batch: %s (%d)" % (strerror(r), r))
+        return out
+
+    def public_from_private_batch_dev(self, d_prv, cnt, d_out_pub, stream=0, dev_idx=0):
+        """Device pointers (ints), enqueue only; 32 bytes per key to d_out_pub."""
+        r = self.lib.fd_ed25519_gpu_public_from_private_batch_dev(self.ctx, dev_idx, d_prv, cnt, d_out_pub, stream)
+        if r:
+            raise GpuError("fd_ed25519_gpu_public_from_private_batch_dev: %s (%d)" % (strerror(r), r))
 
     def sha512_batch_dev(self, d_arena, arena_sz, d_msg, msg_cnt, d_out, stream=0, dev_idx=0):
         r = self.lib.fd_sha512_batch_gpu_dev(self.ctx, dev_idx, d_arena, arena_sz, d_msg, msg_cnt, d_out, stream)

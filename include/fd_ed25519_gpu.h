@@ -310,6 +310,65 @@ int fd_sha256_batch_gpu( fd_ed25519_gpu_t * ctx, uint8_t const * arena, uint64_t
 int fd_sha256_batch_gpu_dev( fd_ed25519_gpu_t * ctx, int dev_idx, uint8_t const * d_arena, uint64_t arena_sz,
                              fd_sha512_gpu_msg_t const * d_msg, uint64_t msg_cnt, uint8_t * d_out, void * stream );
 
+/* ---- Batch signing and key derivation -----------------------------------
+
+   The other half of fd_ed25519.h: fd_ed25519_sign and
+   fd_ed25519_public_from_private (src/ballet/ed25519/fd_ed25519_user.c:
+   4-132), one signature or key per GPU lane.  Signing is deterministic (RFC
+   8032), so the results equal the reference's byte for byte.  As in the
+   reference, the public key of a signature is an input: it is hashed as
+   given and not re-derived from the private key.
+
+   NOT CONSTANT TIME.  [a]B and [r]B are eleven additions of entries of the
+   fixed-base comb table in HBM, and the entries' addresses are the digits
+   of the secret scalars: the memory access pattern depends on the private
+   key and on the nonce, unlike fd_ed25519_scalar_mul_base_const_time, which
+   the reference's signer uses.  That suits load generation (fd_benchg),
+   building test fixtures and bulk signing on a trusted host whose GPU no
+   untrusted party shares or observes.  It does not suit a validator's
+   identity or vote keys on a machine with untrusted tenants.
+
+   The kernels keep the secret scalar, the hash prefix and the nonce in
+   registers only (they build without scratch memory).  The host forms clear
+   their device and page-locked staging copies of the private keys before
+   they return (the reference sanitises its own, fd_ed25519_user.c:51-54,
+   125-129); the _dev forms leave the caller's buffers alone. */
+typedef struct {
+  uint32_t prv_off;   /* 32 bytes: the private key (seed) */
+  uint32_t pub_off;   /* 32 bytes: A, hashed as given     */
+  uint32_t msg_off;
+  uint16_t msg_sz;
+  uint16_t rsvd;      /* 0 */
+} fd_ed25519_sign_desc_t;
+
+/* Signature i (R || S, 64 bytes) of message arena[msg_off, msg_off + msg_sz)
+   goes to out_sig[64 i, 64 i + 64).  Host memory, synchronous, on the
+   context's first device (usable beside pending async batches, as
+   fd_sha512_batch_gpu is); a count above the context's max_batch is split
+   into several launches, a count of 0 returns FD_ED25519_GPU_OK.  A
+   descriptor whose key, public key or message falls outside the arena ->
+   FD_ED25519_GPU_ERR_ARG before anything is launched (out_sig untouched). */
+int fd_ed25519_gpu_sign_batch( fd_ed25519_gpu_t * ctx, uint8_t const * arena, uint64_t arena_sz,
+                               fd_ed25519_sign_desc_t const * desc, uint64_t desc_cnt, uint8_t * out_sig );
+
+/* Device-resident variant (enqueue only, any count; d_arena readable up to
+   align_up(arena_sz,4)+8 bytes, d_out_sig 64*desc_cnt bytes, 4-byte
+   aligned).  No host sees the descriptors: one with a field outside the
+   arena gets 64 zero bytes. */
+int fd_ed25519_gpu_sign_batch_dev( fd_ed25519_gpu_t * ctx, int dev_idx, uint8_t const * d_arena, uint64_t arena_sz,
+                                   fd_ed25519_sign_desc_t const * d_desc, uint64_t desc_cnt, uint8_t * d_out_sig,
+                                   void * stream );
+
+/* Public key i of private key prv[32 i, 32 i + 32) goes to
+   out_pub[32 i, 32 i + 32); same model as fd_ed25519_gpu_sign_batch. */
+int fd_ed25519_gpu_public_from_private_batch( fd_ed25519_gpu_t * ctx, uint8_t const * prv, uint64_t cnt,
+                                              uint8_t * out_pub );
+
+/* Device-resident variant (enqueue only; d_prv and d_out_pub 32*cnt bytes,
+   4-byte aligned). */
+int fd_ed25519_gpu_public_from_private_batch_dev( fd_ed25519_gpu_t * ctx, int dev_idx, uint8_t const * d_prv,
+                                                  uint64_t cnt, uint8_t * d_out_pub, void * stream );
+
 /* ---- Verify stage ---------------------
 
    The verify tile's per-frag logic (src/app/fdctl/run/tiles/fd_verify.c:

@@ -24,6 +24,9 @@
 #   tools/gpu.sh power [bench args]     bench.py in the background; rocm-smi power / clock samples every
 #                                       0.4 s and one amd-smi metric dump once it draws > 1 kW
 #                                       -> gpurun_out/power_$TAG.txt, amdsmi_$TAG.txt, bench_$TAG.json
+#   tools/gpu.sh sign [args]            batch signing / key derivation bench (tools/bench_sign.py) beside the one-shot
+#                                       verify rate of the same batch; lines on stdout and in --out DIR
+#                                       (default profiles/r07/sign/)
 #   tools/gpu.sh run SECONDS CMD...     any other command under its own time limit
 set -e
 mkdir -p gpurun_out
@@ -147,6 +150,8 @@ case "$cmd" in
     wait $P
     grep -E "SOCKET_POWER|PPT_VIOLATION_ACTIVITY" gpurun_out/amdsmi_$T.txt 2>/dev/null || true
     tail -c 300 gpurun_out/bench_$T.json ;;
+  sign)
+    timeout -k 10 ${TLIM:-420} python3 -u tools/bench_sign.py "$@" ;;
   run)
     lim=$1; shift
     timeout -k 10 $lim "$@" ;;

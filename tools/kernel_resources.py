@@ -2,7 +2,8 @@
 """Per-kernel resource / occupancy report from the built code object's metadata.
 
 Reads the amdhsa kernel metadata the assembler embeds (firedancer_amd/build/prod/
-kern.opt.s, the exact code the library ships) and derives, per kernel, the
+kern.opt.s and, for the signing kernels, sign.opt.s beside it: the exact code the
+library ships) and derives, per kernel, the
 occupancy limits on gfx950: 512 VGPRs per lane per SIMD (unified arch + acc file,
 allocation granule 8), 160 KB of LDS per CU, at most 8 waves per SIMD.  With the
 SQ counters of profiles/r02/pmc_sq.json it adds the achieved mean waves per SIMD
@@ -58,7 +59,9 @@ def main():
         build = dict(kv.split("=", 1) for kv in t.split())
     rep = {"source": os.path.relpath(ASM, REPO), "build": build, "model": "gfx950: 512 VGPRs/SIMD lane, granule 8; "
            "160 KB LDS/CU; 8 waves/SIMD; 4 SIMDs/CU; 256 CUs", "kernels": {}}
-    for k in metadata(ASM):
+    # the code object's second translation unit (the signing kernels) sits beside the first
+    sign = os.path.join(os.path.dirname(ASM), "sign.opt.s")
+    for k in metadata(ASM) + (metadata(sign) if os.path.basename(ASM) == "kern.opt.s" and os.path.exists(sign) else []):
         rep["kernels"][k[".name"]] = limits(k)
     pmc = os.environ.get("KR_PMC", "")          # a pmc_sq.json for the achieved waves per SIMD
     if pmc and os.path.exists(pmc):
